@@ -42,6 +42,30 @@ def build_agent(num_env, seed):
     return exp.agent, cfg
 
 
+def dump_outputs(path, agent, metrics):
+    """--dump-outputs: what the last timed step handed back, one float64 /
+    float32 .npy per name -- the metrics mapping `agent.step()` returned
+    (metric.<key>.npy; not its wall and device times, which no two runs
+    share) and the networks that step left behind (policy.<i>.npy,
+    critic.<i>.npy in `parameters` order, in their own dtype).  The agent,
+    its env and its noise are seeded, so two builds run with the same
+    arguments can be compared file by file.  A few hundred kB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in dict(metrics).items():
+        if k.endswith("_time"):
+            continue
+        if torch.is_tensor(v):
+            v = v.detach().cpu().numpy()
+        np.save(os.path.join(path, "metric.%s.npy" % k.replace("/", "_")),
+                np.asarray(v, dtype=np.float64))
+    for name, params in (("policy", agent.policy.parameters),
+                         ("critic", agent.critic.parameters)):
+        for i, p in enumerate(params):
+            np.save(os.path.join(path, "%s.%d.npy" % (name, i)),
+                    p.detach().cpu().numpy())
+
+
 def time_balance_iteration(agent, sync):
     """Wall time (ms, synchronised on both sides) of ONE iteration with the
     policy balance check (num_iterations % balance_check == 1: every policy
@@ -942,6 +966,8 @@ def self_launch(args):
         base_cmd += ["--critic-arith", args.critic_arith]
     if getattr(args, "no_configs", False):
         base_cmd.append("--no-configs")
+    if getattr(args, "dump_outputs", None):
+        base_cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if getattr(args, "scaling", "weak") != "weak":
         base_cmd += ["--scaling", args.scaling]
     base_env = dict(os.environ)
@@ -1026,6 +1052,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the K timed steps, write what the last of them "
+                         "returned and the networks it left behind as "
+                         "DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-full", action="store_true",
                     help="cpu_baseline additionally times ONE oracle step at "
@@ -1181,6 +1211,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     tlib.call("tce_marker", 2, tlib.stream())
+    if args.dump_outputs and rank == 0:     # (before any further step runs)
+        dump_outputs(args.dump_outputs, agent, results[-1])
     for res in results:
         pol_time += res["update_policy_time"]
         crit_time += res["update_critic_time"]      # device time (HIP events)

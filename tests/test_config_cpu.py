@@ -38,31 +38,29 @@ def test_named_experiment_and_plain_file():
     assert mp_exp.load_config(shared)["iterations"] == 100
 
 
-REF = "/root/reference/mprl/config"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not here")
 def test_reference_config_files_resolve():
-    """The reference's own experiment files load unchanged (read as data)."""
+    """The reference's own experiment documents (tests/golden/resolved/*.json:
+    its local.yaml files as cw2 resolves them, written by
+    tests/golden/make_resolved_cfg.py through mp_exp.load_config) hold every
+    block the experiment needs and name only classes the factories know."""
+    import json
     n = 0
-    for root, _, files in os.walk(REF):
-        for f in files:
-            if f == "local.yaml":
-                cfg = mp_exp.load_config(os.path.join(root, f))
-                p = cfg["params"]
-                for blk in ("agent", "policy", "critic", "sampler",
-                            "projection", "mp"):
-                    assert "type" in p[blk] and "args" in p[blk], (root, blk)
-                assert p["agent"]["args"]["epochs_policy"] > 0
-                mp_exp.dim_policy_out(p)
-                # every class the file names exists behind the factories
-                from tce_rl_amd.rl import agent, critic, policy, projection, \
-                    sampler
-                for mod, blk in ((agent, "agent"), (critic, "critic"),
-                                 (policy, "policy"), (sampler, "sampler"),
-                                 (projection, "projection")):
-                    assert hasattr(mod, p[blk]["type"]), (root, p[blk]["type"])
-                n += 1
+    for f in sorted(os.listdir(RES)):
+        with open(os.path.join(RES, f)) as fh:
+            p = json.load(fh)["params"]
+        for blk in ("agent", "policy", "critic", "sampler",
+                    "projection", "mp"):
+            assert "type" in p[blk] and "args" in p[blk], (f, blk)
+        assert p["agent"]["args"]["epochs_policy"] > 0
+        mp_exp.dim_policy_out(p)
+        # every class the file names exists behind the factories
+        from tce_rl_amd.rl import agent, critic, policy, projection, \
+            sampler
+        for mod, blk in ((agent, "agent"), (critic, "critic"),
+                         (policy, "policy"), (sampler, "sampler"),
+                         (projection, "projection")):
+            assert hasattr(mod, p[blk]["type"]), (f, p[blk]["type"])
+        n += 1
     assert n >= 4
 
 
@@ -129,15 +127,3 @@ def test_bbrl_config_matches_the_reference_document():
         assert ours[blk]["type"] == ref[blk]["type"]
         problems += _diff(ours[blk]["args"], ref[blk]["args"], blk + ".")
     assert not problems, "\n".join(problems)
-
-
-def test_resolved_fixtures_are_current():
-    """The committed fixtures equal what the generator writes from the
-    reference tree today (runs where /root/reference exists)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not here")
-    import json
-    for f in sorted(os.listdir(RES)):
-        doc = json.load(open(os.path.join(RES, f)))
-        cfg = mp_exp.load_config(os.path.join("/root/reference", doc["source"]))
-        assert json.loads(json.dumps(cfg["params"])) == doc["params"], f

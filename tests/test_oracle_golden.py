@@ -8,6 +8,21 @@ from oracle.prodmp_oracle import ProDMPOracle, pair_log_prob
 
 T = torch.as_tensor
 
+# The vectors were written by one host; the oracle runs on whichever host runs
+# the tests.  Index arithmetic, copies and torch's own element-wise kernels give
+# the same bits everywhere and are compared bit for bit.  What goes through the
+# host's math library (BLAS / LAPACK / vector exp and log pick their code path by
+# CPU model) is float32 linear algebra: right to a few ulp of the LARGEST entry
+# times the condition of the problem, not entry by entry.
+
+
+def assert_close_to_scale(actual, desired, tol):
+    """max |actual - desired| <= tol * max |desired|"""
+    actual, desired = np.asarray(actual), np.asarray(desired)
+    assert actual.shape == desired.shape
+    err = float(np.abs(actual - desired).max())
+    assert err <= tol * float(np.abs(desired).max()), (err, tol)
+
 
 def test_pred_pairs_bit_exact(golden):
     g = golden("pred_pairs")
@@ -62,9 +77,20 @@ def test_cholesky_head(golden):
         for std_only in (False, True):
             tag = f"K{K}_{'diag' if std_only else 'full'}"
             L = O.vector_to_cholesky(T(g[f"vec_{tag}"]), K, 1e-5, std_only)
-            assert np.array_equal(L.numpy(), g[f"L_{tag}"])
+            # below the diagonal: copies of the vector, above: zeros
+            off = ~np.eye(K, dtype=bool)
+            assert np.array_equal(L.numpy()[..., off], g[f"L_{tag}"][..., off])
+            np.testing.assert_array_max_ulp(            # softplus
+                L.diagonal(dim1=-2, dim2=-1).numpy(),
+                np.diagonal(g[f"L_{tag}"], axis1=-2, axis2=-1), maxulp=2)
             back = O.cholesky_to_vector(L, 1e-5, std_only)
-            assert np.array_equal(back.numpy(), g[f"back_{tag}"])
+            assert np.array_equal(back.numpy()[..., K:],
+                                  g[f"back_{tag}"][..., K:])
+            # log(exp(d - lb) - 1) of diagonals d of order 1: the subtraction
+            # leaves an absolute error of a few float32 ulp of 1
+            np.testing.assert_allclose(back.numpy()[..., :K],
+                                       g[f"back_{tag}"][..., :K],
+                                       rtol=1e-6, atol=4e-6)
     v = O.initial_variance_vector(24, False)
     assert np.array_equal(v[:24].numpy(), g["init_var_full_K24"])
     assert float(v[24:].abs().max()) == 0
@@ -98,19 +124,19 @@ def test_mvn(golden):
         np.testing.assert_allclose(lp.detach().numpy(), g[f"logp_K{K}"],
                                    rtol=1e-6)
         (lp * T(g[f"w_K{K}"])).sum().backward()
-        np.testing.assert_allclose(mean.grad.numpy(), g[f"dmean_K{K}"],
-                                   rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(L.grad.numpy(), g[f"dL_K{K}"], rtol=1e-5,
-                                   atol=1e-6)
+        # triangular solves with L and L^T (the K 36 factor is the worse
+        # conditioned: two hosts' float32 gradients differ by 4e-5 of scale)
+        tol = {20: 5e-6, 36: 2e-4}[K]
+        assert_close_to_scale(mean.grad.numpy(), g[f"dmean_K{K}"], tol)
+        assert_close_to_scale(L.grad.numpy(), g[f"dL_K{K}"], tol)
+        assert np.array_equal(L.grad.numpy() == 0, g[f"dL_K{K}"] == 0)
         Ld = L.detach()
         np.testing.assert_allclose(O.mvn_entropy(mean.detach(), Ld).numpy(),
                                    g[f"ent_K{K}"], rtol=1e-6)
-        np.testing.assert_allclose(O.covariance(Ld).numpy(), g[f"cov_K{K}"],
-                                   rtol=1e-6, atol=1e-7)
+        assert_close_to_scale(O.covariance(Ld).numpy(), g[f"cov_K{K}"], 1e-6)
         np.testing.assert_allclose(O.log_determinant(Ld).numpy(),
                                    g[f"logdet_K{K}"], rtol=1e-6)
-        np.testing.assert_allclose(O.precision(Ld).numpy(), g[f"prec_K{K}"],
-                                   rtol=1e-5, atol=1e-5)
+        assert_close_to_scale(O.precision(Ld).numpy(), g[f"prec_K{K}"], 5e-6)
         np.testing.assert_allclose(
             O.maha(mean.detach(), T(g[f"other_K{K}"]), Ld).numpy(),
             g[f"maha_K{K}"], rtol=1e-6)
@@ -122,13 +148,13 @@ def test_mlp_and_losses(golden):
         params = [(T(g[f"{act}_p{2 * i}"]), T(g[f"{act}_p{2 * i + 1}"]))
                   for i in range(3)]
         y = O.mlp_forward(params, T(g[f"{act}_x"]), act)
-        np.testing.assert_allclose(y.numpy(), g[f"{act}_y"], rtol=1e-6,
-                                   atol=1e-7)
-        # same init from the same seed (orthogonal, zero bias, gains)
+        assert_close_to_scale(y.numpy(), g[f"{act}_y"], 2e-6)
+        # same init from the same seed (orthogonal, zero bias, gains): the same
+        # random draws through the host's QR factorisation
         torch.manual_seed(int(g[f"{act}_seed"]))
         init = O.mlp_init(11, 1, [16, 16], 1.0)
         for i, (W, b) in enumerate(init):
-            assert np.array_equal(W.numpy(), g[f"{act}_p{2 * i}"])
+            assert_close_to_scale(W.numpy(), g[f"{act}_p{2 * i}"], 1e-5)
             assert np.array_equal(b.numpy(), g[f"{act}_p{2 * i + 1}"])
     v, r, o = T(g["vl_values"]), T(g["vl_returns"]), T(g["vl_old"])
     np.testing.assert_allclose(O.value_loss(v, r, o, 0.0), g["vl_unclipped"],
@@ -182,5 +208,7 @@ def test_pair_logprob_plumbing(golden):
                                    g[f"{tag}_traj"], rtol=1e-6, atol=1e-6)
         lp = pair_log_prob(mp, a("traj"), a("mean"), a("L"), a("times"),
                            a("t0"), a("y0"), a("v0"), a("pairs"))
+        # float32 solves against the pair covariance: the stored values are
+        # themselves 1.7e-4 away from this function evaluated in float64
         np.testing.assert_allclose(lp.numpy(), g[f"{tag}_logp"], rtol=1e-5,
-                                   atol=1e-5)
+                                   atol=6e-4)
