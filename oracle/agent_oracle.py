@@ -8,6 +8,14 @@ TEST INFRASTRUCTURE ONLY -- see ``oracle/__init__.py``.  Used by
 ``bench.py``'s ``cpu_baseline`` leg (kind "port") and by tests; follows
 ``mprl/rl/agent/temporal_correlated_agent.py:38-100,323-639`` and
 ``mprl/rl/sampler/temporal_correlated_sampler.py:91-344``.
+
+Several episodes per env and rollout (``episodes``; the sampler loops of
+temporal_correlated_sampler.py:119,169-344 and black_box_sampler.py:158-249):
+one pair draw per rollout, episode e+1 starts from the env's next reset, the
+observation statistics are updated AND applied episode by episode (training
+only), the MDP reward uses each episode's own event flags, and every tensor
+is concatenated over the episodes (episode-major, env-minor), so the update
+sees ``num_env * episodes`` rows.
 """
 import numpy as np
 import torch
@@ -19,8 +27,12 @@ from .prodmp_oracle import ProDMPOracle, pair_log_prob
 
 
 class OracleTCE:
-    def __init__(self, cfg, num_env, seed=0, total_iterations=7600):
-        """cfg: the ``params`` dict of tce_rl_amd.config.tce_config (same
+    def __init__(self, cfg, num_env, seed=0, total_iterations=7600, episodes=1,
+                 test_episodes=1):
+        """episodes / test_episodes: episodes per env of a training /
+        evaluation rollout (the sampler's ``episodes_per_train_env`` /
+        ``episodes_per_test_env``).
+        cfg: the ``params`` dict of tce_rl_amd.config.tce_config (same
         structure as the reference YAML).  Every agent / policy switch of the
         reference is honoured: ``clip_critic`` / ``clip_advantages`` /
         ``clip_grad_norm``, the three ``segment_advantage`` modes,
@@ -81,8 +93,13 @@ class OracleTCE:
         self.initial_entropy = None
         self.it = 0
         self.gen = torch.Generator().manual_seed(seed)
-        self.forced_reset = None      # (goal, init_pos) injected by tests
-        self.forced_eps = None        # parameter noise injected by tests
+        self.episodes, self.test_episodes = int(episodes), int(test_episodes)
+        # injected by tests: (goal, init_pos), or a sequence of such pairs, one
+        # per reset of a rollout (the env resets at the start and after every
+        # episode; the last reset's observation is never used);
+        # parameter noise [N, K], or a sequence of them, one per episode
+        self.forced_reset = None
+        self.forced_eps = None
         self.last = {}                # rollout tensors of the last step
 
     def _mlp(self, net, x, act):
@@ -100,10 +117,11 @@ class OracleTCE:
                                      self.std_only).expand(obs.shape[0], -1, -1)
         return mean, L
 
-    def _reset(self):
+    def _reset(self, index=0):
+        """The env's reset number `index` of this rollout."""
         r = lambda *s: torch.rand(*s, generator=self.gen, dtype=self.dtype)
         if self.forced_reset is not None:           # tests: same env state
-            self.goal, pos = self.forced_reset
+            self.goal, pos = _reset_entry(self.forced_reset, index)
         else:
             self.goal = r(self.N, self.dof) * 2 - 1
             pos = 0.1 * (r(self.N, self.dof) * 2 - 1)
@@ -118,45 +136,56 @@ class OracleTCE:
         feeds the critic raw states and leaves the statistics alone.  The pair
         offsets are drawn in both cases (:136)."""
         N, T, D2 = self.N, self.T, 2 * self.dof
+        episodes = self.episodes if training else self.test_episodes
+        keys = ("step_actions", "segment_log_prob_estimate", "step_values",
+                "step_rewards", "episode_reward", "segment_params_mean",
+                "segment_params_L", "step_states", "segment_state", "times",
+                "success")
+        out = {k: [] for k in keys}
         with torch.no_grad():
-            s0 = self._reset()
+            s0 = self._reset(0)
             pairs = O.get_time_pairs(T, dict(num_select=25,
                                              fixed_interval=True))
-            t0 = s0[:, -D2 - 1]
-            y0, v0 = s0[:, -D2:-self.dof], s0[:, -self.dof:]
-            mean_old, L_old = self._policy(s0[:, :-D2])
-            times = O.get_times(t0, self.dt, T)
-            if deterministic:
-                eps = torch.zeros(N, self.K, dtype=self.dtype)
-            elif self.forced_eps is not None:
-                eps = self.forced_eps
-            else:
-                eps = torch.randn(N, self.K, generator=self.gen,
-                                  dtype=self.dtype)
-            pos, vel = self.mp.sample_trajectories(times, mean_old, L_old, t0,
-                                                   y0, v0, eps)
-            actions = torch.cat([pos, vel], -1)
-            lp_old = pair_log_prob(self.mp, actions, mean_old, L_old, times,
-                                   t0, y0, v0, pairs)
-            states, rewards, flags, metrics = E.rollout(
-                self.task, actions, s0, self.dof, self.d_task, self.dt)
-            episode_reward = rewards.sum(-1)
-            if self.task == "table_tennis":     # make_mdp_reward on hit_ball
-                rewards = O.make_mdp_reward(rewards, flags)
-            if training:
-                self.rms.update(states.view(-1, self.D))
-                nstates = self.rms.normalise(states)
-            else:
-                nstates = states
-            values = self._mlp(self.cnet, nstates[..., :-D2],
-                               self.c_act).squeeze(-1)
-        return dict(step_actions=actions, segment_log_prob_estimate=lp_old,
-                    step_values=values, step_rewards=rewards,
-                    episode_reward=episode_reward,
-                    segment_reward=rewards.sum(-1), pred_pairs=pairs,
-                    segment_params_mean=mean_old, segment_params_L=L_old,
-                    step_states=nstates, segment_state=s0, times=times,
-                    success=metrics[:, 0])
+            for e in range(episodes):
+                t0 = s0[:, -D2 - 1]
+                y0, v0 = s0[:, -D2:-self.dof], s0[:, -self.dof:]
+                mean_old, L_old = self._policy(s0[:, :-D2])
+                times = O.get_times(t0, self.dt, T)
+                if deterministic:
+                    eps = torch.zeros(N, self.K, dtype=self.dtype)
+                elif self.forced_eps is not None:
+                    eps = _eps_entry(self.forced_eps, e)
+                else:
+                    eps = torch.randn(N, self.K, generator=self.gen,
+                                      dtype=self.dtype)
+                pos, vel = self.mp.sample_trajectories(times, mean_old, L_old,
+                                                       t0, y0, v0, eps)
+                actions = torch.cat([pos, vel], -1)
+                lp_old = pair_log_prob(self.mp, actions, mean_old, L_old,
+                                       times, t0, y0, v0, pairs)
+                states, rewards, flags, metrics = E.rollout(
+                    self.task, actions, s0, self.dof, self.d_task, self.dt)
+                episode_reward = rewards.sum(-1)
+                if self.task == "table_tennis":  # make_mdp_reward on hit_ball
+                    rewards = O.make_mdp_reward(rewards, flags)
+                if training:
+                    self.rms.update(states.view(-1, self.D))
+                    nstates = self.rms.normalise(states)
+                else:
+                    nstates = states
+                values = self._mlp(self.cnet, nstates[..., :-D2],
+                                   self.c_act).squeeze(-1)
+                for k, v in zip(keys, (actions, lp_old, values, rewards,
+                                       episode_reward, mean_old, L_old,
+                                       nstates, s0, times, metrics[:, 0])):
+                    out[k].append(v)
+                if e + 1 < episodes:    # (the reset after the last: unused)
+                    s0 = self._reset(e + 1)
+        ro = {k: v[0] if len(v) == 1 else torch.cat(v, 0)
+              for k, v in out.items()}
+        ro["segment_reward"] = ro["step_rewards"].sum(-1)
+        ro["pred_pairs"] = pairs
+        return ro
 
     def evaluate(self):
         """AbstractAgent.evaluate(evaluate_deterministic=True)
@@ -165,7 +194,8 @@ class OracleTCE:
 
     def step(self):
         self.it += 1
-        N, T, D2 = self.N, self.T, 2 * self.dof
+        # N: the rows of the dataset (envs x episodes, episode-major)
+        N, T, D2 = self.N * self.episodes, self.T, 2 * self.dof
         a = self.a
         ro = self.rollout(training=True)
         actions, lp_old, values = ro["step_actions"], \
@@ -190,7 +220,9 @@ class OracleTCE:
                          step_values=values, step_rewards=rewards,
                          step_advantages=adv, step_returns=ret,
                          segment_advantage=seg_adv, pred_pairs=pairs,
-                         segment_params_mean=mean_old, step_states=nstates)
+                         segment_params_mean=mean_old, step_states=nstates,
+                         segment_state=s0, obs_rms_mean=self.rms.mean, obs_rms_var=self.rms.var,
+                         obs_rms_count=self.rms.count)
         # ---- critic epochs (temporal_correlated_agent.py:323-379)
         import numpy as np
         cs = nstates[:, :-1, :-D2].reshape(N * T, -1)
@@ -296,6 +328,18 @@ class OracleTCE:
         return N * T
 
 
+def _reset_entry(forced, index):
+    """(goal, pos) of reset `index`: tests inject one pair for every reset, or
+    a sequence with one pair per reset."""
+    return forced if torch.is_tensor(forced[0]) else forced[index]
+
+
+def _eps_entry(forced, index):
+    """Noise of episode `index`: one tensor for every episode, or a sequence
+    with one per episode."""
+    return forced if torch.is_tensor(forced) else forced[index]
+
+
 class OracleBBRL:
     """CPU restatement of one ``BlackBoxAgent.step()``: episode-level policy
     (param-space Gaussian, diagonal or full), the env turns the sampled MP
@@ -308,7 +352,8 @@ class OracleBBRL:
                  act, std_only, min_std, out_layer_gain, lr, epochs, mean_bound,
                  cov_bound, tr_coeff, set_variance, norm_advantages=True,
                  clip_advantages=0.0, clip_critic=0.0, dtype=torch.float32,
-                 balance=False, weight_decay=0.0, num_minibatchs=1):
+                 balance=False, weight_decay=0.0, num_minibatchs=1,
+                 episodes=1):
         mpa = dict(mp_args)
         mpa.pop("dtype", None), mpa.pop("device", None)
         self.mp = ProDMPOracle(dtype=dtype, **mpa)
@@ -345,6 +390,11 @@ class OracleBBRL:
         self.clip_critic = clip_critic
         # critic minibatches (black_box_agent.py:124-131; class default 10)
         self.num_minibatchs = int(num_minibatchs)
+        # episodes per env and step (black_box_sampler.py:158-249), every
+        # tensor concatenated over them; forced_reset / forced_eps: one
+        # (goal, pos) pair / noise tensor, or a sequence with one entry per
+        # reset / episode, as in OracleTCE
+        self.episodes = int(episodes)
         self.forced_reset = self.forced_eps = None
         self.last = {}
 
@@ -360,21 +410,31 @@ class OracleBBRL:
 
     def step(self):
         N, T = self.N, self.T
-        goal, pos0 = self.forced_reset
+        rows = {k: [] for k in ("obs", "mean", "L", "action", "lp", "values",
+                                "reward")}
         with torch.no_grad():
-            v0 = torch.zeros(N, self.dof, dtype=self.dtype)
-            full0 = E.reset_obs(self.task, self.D, goal, pos0, v0)
-            obs = full0[:, :self.D]
-            mean_old, L_old = self._policy(obs)
-            action = O.mvn_rsample(mean_old, L_old, self.forced_eps)
-            lp_old = O.mvn_log_prob(action, mean_old, L_old)
-            values = self._mlp(self.cnet, obs).squeeze(-1)
-            t0 = torch.zeros(N, dtype=self.dtype)
-            pos, vel = self.mp.traj(O.get_times(t0, self.dt, T), action, t0,
-                                    pos0, v0)
-            _, rew, _, _ = E.rollout(self.task, torch.cat([pos, vel], -1),
-                                     full0, self.dof, self.D, self.dt)
-            reward = rew.sum(-1)
+            for e in range(self.episodes):
+                goal, pos0 = _reset_entry(self.forced_reset, e)
+                v0 = torch.zeros(N, self.dof, dtype=self.dtype)
+                full0 = E.reset_obs(self.task, self.D, goal, pos0, v0)
+                obs = full0[:, :self.D]
+                mean_old, L_old = self._policy(obs)
+                action = O.mvn_rsample(mean_old, L_old,
+                                       _eps_entry(self.forced_eps, e))
+                lp_old = O.mvn_log_prob(action, mean_old, L_old)
+                values = self._mlp(self.cnet, obs).squeeze(-1)
+                t0 = torch.zeros(N, dtype=self.dtype)
+                pos, vel = self.mp.traj(O.get_times(t0, self.dt, T), action,
+                                        t0, pos0, v0)
+                _, rew, _, _ = E.rollout(self.task, torch.cat([pos, vel], -1),
+                                         full0, self.dof, self.D, self.dt)
+                for k, v in zip(rows, (obs, mean_old, L_old, action, lp_old,
+                                       values, rew.sum(-1))):
+                    rows[k].append(v)
+            obs, mean_old, L_old, action, lp_old, values, reward = (
+                v[0] if len(v) == 1 else torch.cat(v, 0)
+                for v in rows.values())
+            N = N * self.episodes       # rows of the dataset from here on
             adv = O.bbrl_advantage(reward, values, self.norm_advantages,
                                    self.clip_advantages)
         self.last = dict(segment_action=action, segment_log_prob=lp_old,

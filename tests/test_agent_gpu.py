@@ -18,14 +18,66 @@ def _close(name, got, want, rel):
     assert err <= rel * scale, (name, err, rel * scale)
 
 
+def _forced_state(N, dof, K, td, episodes, seed):
+    """Env state and parameter noise for both sides: (goal, pos0) per reset of
+    a rollout -- an env resets at the start and after every episode, so
+    ``episodes + 1`` of them, the last one unused -- and the noise per episode,
+    all distinct.  (One episode: the draws the one-episode tests always
+    made, the reset after the episode hands out the same state again.)"""
+    g = torch.Generator().manual_seed(seed)
+    draw_reset = lambda: (
+        (torch.rand(N, dof, generator=g) * 2 - 1).to(td),
+        (0.1 * (torch.rand(N, dof, generator=g) * 2 - 1)).to(td))
+    draw_eps = lambda: torch.randn(N, K, generator=g).to(td)
+    resets, eps = [draw_reset()], [draw_eps()]
+    if episodes == 1:
+        return resets * 2, eps
+    resets += [draw_reset() for _ in range(episodes)]
+    eps += [draw_eps() for _ in range(episodes - 1)]
+    return resets, eps
+
+
+def _force_resets(env, resets, td):
+    """env.reset() hands out resets[0], resets[1], ... and starts over after
+    the last (one rollout = one pass)."""
+    N, dof = resets[0][1].shape
+    turn = [0]
+
+    def reset():
+        goal, pos0 = resets[turn[0] % len(resets)]
+        turn[0] += 1
+        env.goal = goal.cuda()
+        z = torch.zeros(N, dof, device="cuda", dtype=td)
+        return env._obs(torch.zeros(N, device="cuda", dtype=td), pos0.cuda(), z)
+    env.reset = reset
+
+
+def _force_noise(policy, eps):
+    """policy.sample() uses eps[0], eps[1], ... for its stochastic calls and
+    starts over after the last (one training rollout = one pass)."""
+    orig, turn = policy.sample, [0]
+
+    def sample(**kw):
+        if kw.get("use_mean"):
+            return orig(**kw)
+        e = eps[turn[0] % len(eps)]
+        turn[0] += 1
+        return orig(**kw, eps=e.cuda())
+    policy.sample = sample
+
+
 def build(num_env, epochs, overlap, env="metaworld", num_basis=5,
-          dtype="float32", **agent_kw):
+          dtype="float32", episodes=1, test_episodes=1, **agent_kw):
     """agent_kw: agent constructor arguments; the keys ``_contextual`` /
-    ``_std_only`` switch the policy's covariance head instead."""
+    ``_std_only`` switch the policy's covariance head instead.  episodes /
+    test_episodes: the sampler's ``episodes_per_train_env`` /
+    ``episodes_per_test_env``."""
     from tce_rl_amd.config import tce_config
     from tce_rl_amd.mp_exp import MPExperiment
     cfg = tce_config(env, num_env=num_env, num_basis=num_basis, epochs=epochs,
                      evaluation_interval=0, dtype=dtype)
+    cfg["params"]["sampler"]["args"].update(
+        episodes_per_train_env=episodes, episodes_per_test_env=test_episodes)
     agent_kw = dict(agent_kw)
     vna = cfg["params"]["policy"]["args"]["variance_net_args"]
     if agent_kw.pop("_contextual", False):
@@ -196,13 +248,19 @@ def test_agent_step_matches_cpu_oracle_bf16x3_critic(overlap):
 
 
 def _agent_vs_oracle(overlap, fused, graph, env, nb, dtype="float32",
-                     iterations=1, rel_scale=1.0, num_env=16, epochs=3, **kw):
+                     iterations=1, rel_scale=1.0, num_env=16, epochs=3,
+                     episodes=1, critic_vs_oracle=True, **kw):
+    """episodes: per env and rollout, each from its own forced reset with its
+    own noise -- the dataset has ``num_env * episodes`` rows.
+    critic_vs_oracle False: the critic's minibatches are not the oracle's
+    (device-drawn permutations), its parameters are not compared."""
     from oracle.agent_oracle import OracleTCE
     N, EPOCHS = num_env, epochs
     agent, cfg = build(N, EPOCHS, overlap, env=env, num_basis=nb, dtype=dtype,
                        fused_policy_objective=fused,
-                       graph_policy_update=graph, **kw)
-    oracle = OracleTCE(cfg["params"], N, total_iterations=cfg["iterations"])
+                       graph_policy_update=graph, episodes=episodes, **kw)
+    oracle = OracleTCE(cfg["params"], N, total_iterations=cfg["iterations"],
+                       episodes=episodes)
     # identical weights
     with torch.no_grad():
         for po, pg in zip(oracle.pnet, agent.policy.mean_net.parameters()):
@@ -213,23 +271,12 @@ def _agent_vs_oracle(overlap, fused, graph, env, nb, dtype="float32",
                           agent.policy.variance_net.parameters()):
             po.copy_(pg.cpu())
     # identical env state and noise
-    g = torch.Generator().manual_seed(7)
-    dof = agent.policy.num_dof
     td = torch.float64 if dtype == "float64" else torch.float32
-    goal = (torch.rand(N, dof, generator=g) * 2 - 1).to(td)
-    pos0 = (0.1 * (torch.rand(N, dof, generator=g) * 2 - 1)).to(td)
-    eps = torch.randn(N, agent.policy.dim_out, generator=g).to(td)
-    env = agent.sampler.train_envs
-
-    def reset():
-        env.goal = goal.cuda()
-        z = torch.zeros(N, dof, device="cuda", dtype=td)
-        return env._obs(torch.zeros(N, device="cuda", dtype=td), pos0.cuda(), z)
-    env.reset = reset
-    orig_sample = agent.policy.sample
-    agent.policy.sample = lambda **kw: orig_sample(**kw, eps=eps.cuda())
-    oracle.forced_reset = (goal, pos0)
-    oracle.forced_eps = eps
+    resets, eps = _forced_state(N, agent.policy.num_dof, agent.policy.dim_out,
+                                td, episodes, 7)
+    _force_resets(agent.sampler.train_envs, resets, td)
+    _force_noise(agent.policy, eps)
+    oracle.forced_reset, oracle.forced_eps = resets, eps
 
     captured = {}
     orig_pd = agent.process_dataset
@@ -295,7 +342,9 @@ def _agent_vs_oracle(overlap, fused, graph, env, nb, dtype="float32",
            ref["segment_log_prob_estimate"], 1e-5)
     # parameters after EPOCHS critic + policy updates
     for pg, po in zip(agent.critic.net.parameters(), oracle.cnet):
-        close("critic", pg.detach().cpu(), po.detach(), 1e-7 if f64 else 5e-5)
+        if critic_vs_oracle:
+            close("critic", pg.detach().cpu(), po.detach(),
+                  1e-7 if f64 else 5e-5)
     for pg, po in zip(agent.policy.mean_net.parameters(), oracle.pnet):
         close("policy", pg.detach().cpu(), po.detach(), 1e-6 if f64 else 3e-4)
     for pg, po in zip(agent.policy.variance_net.parameters(),
@@ -303,7 +352,102 @@ def _agent_vs_oracle(overlap, fused, graph, env, nb, dtype="float32",
         close("variance", pg.detach().cpu(), po.detach(),
               1e-6 if f64 else 3e-5)
     assert np.isfinite(res["critic_loss_mean"])
+    if episodes > 1:
+        _check_episode_rows(agent, oracle, captured, N, episodes)
     return agent, oracle, res
+
+
+def _check_episode_rows(agent, oracle, captured, N, episodes):
+    """What only shows with several episodes: the dataset has N * episodes
+    rows, every episode was normalised with the observation statistics of ITS
+    moment, and the statistics have seen every row once (tolerances: those of
+    tests/test_rollout_gpu.py for the statistics and the normalised rows)."""
+    ref, rms = oracle.last, agent.sampler.obs_rms
+    T = agent.sampler.num_times
+    R = N * episodes
+    assert captured["step_actions"].shape[0] == R
+    assert captured["step_states"].shape[:2] == (R, T)
+    # statistics: float32 at tests/test_rollout_gpu.py's 2e-5 (seen here:
+    # 1.4e-7, table tennis variance).  float64: THERE the kernel gets the
+    # oracle's very rows and the bound is 1e-10; HERE the rows come from each
+    # side's own ProDMP table, which agree to ~1e-6 (see _agent_vs_oracle:
+    # step_actions seen 2.2e-7 in this float64 case), so the statistics cannot
+    # agree to 1e-10 -- seen 9.5e-10 (variance, after four merges), bound 1e-8
+    f64 = ref["step_states"].dtype == torch.float64
+    tol = 1e-8 if f64 else 2e-5
+    _close("obs_rms_mean", rms.mean.cpu(), ref["obs_rms_mean"], tol)
+    _close("obs_rms_var", rms.var.cpu(), ref["obs_rms_var"], tol)
+    assert abs(rms.count - ref["obs_rms_count"]) < 1e-6
+    assert rms.count == pytest.approx(
+        1e-4 + agent.num_iterations * R * (T + 1), rel=1e-12)
+    # normalised rows at test_rollout_gpu.py's 1e-5 (seen: 3.5e-6 float32,
+    # 6.3e-7 float64 -- the actions' deviation divided by the columns' std)
+    stol = 1e-5
+    _close("step_states", captured["step_states"], ref["step_states"][:, :-1],
+           stol)
+    # the first episode's rows under the FINAL statistics are something else:
+    # the comparison above does tell "per episode" from "once at the end"
+    first = ref["segment_state"][:N]
+    with_final = (first - ref["obs_rms_mean"]) / torch.sqrt(
+        ref["obs_rms_var"] + 1e-8)
+    assert (ref["step_states"][:N, 0] - with_final).abs().max() > 100 * stol
+
+
+EPISODE_CASES = {
+    # the statistics carried over two iterations (four merges), float64
+    "box_push_f64_2x2": dict(env="box_push", nb=3, dtype="float64", num_env=12,
+                             episodes=2, iterations=2),
+    # MDP reward with each episode's own hit_ball flags; 33 rows
+    "table_tennis_3": dict(env="table_tennis", nb=3, num_env=11, episodes=3),
+    # 22 rows x 500 steps in 4 minibatches of numpy's permutation
+    "metaworld_minibatches": dict(env="metaworld", nb=5, num_env=11,
+                                  episodes=2, num_minibatchs=4),
+    # per-row Cholesky factors: the concatenation materialises [N * E, K, K]
+    "metaworld_contextual": dict(env="metaworld", nb=5, num_env=11, episodes=2,
+                                 _contextual=True),
+}
+
+
+@pytest.mark.parametrize("case", sorted(EPISODE_CASES))
+def test_agent_step_of_several_episodes_matches_cpu_oracle(case, monkeypatch):
+    """agent.step() with ``episodes_per_train_env`` > 1 against the CPU oracle
+    running the same episodes: every episode from its own reset with its own
+    noise, ONE pair draw, observation statistics updated and applied episode
+    by episode, rows concatenated episode-major -- and N * E rows (a number
+    the kernels do not tile by) through GAE, the segment advantage, the critic
+    and the policy epochs.  Tolerances: the one-episode table, x 2 for a second
+    iteration."""
+    kw = dict(EPISODE_CASES[case])
+    env, nb = kw.pop("env"), kw.pop("nb")
+    iters = kw.get("iterations", 1)
+    spy = _PathSpy(monkeypatch)
+    agent, oracle, res = _agent_vs_oracle(
+        True, True, False, env, nb, epochs=2, rel_scale=float(iters), **kw)
+    if kw.get("_contextual"):
+        assert agent.last_policy_plan.kind == "op_by_op"
+    if "num_minibatchs" in kw:
+        assert tuple(agent.last_critic_plan)[:2] == ("fused-narrow", 4)
+        assert (spy.direct, spy.node) == (2 * iters, 0)
+
+
+def test_agent_step_of_several_episodes_with_device_drawn_minibatches():
+    """The same with ``minibatch_permutation: device`` (a keyed permutation of
+    the N * E * T rows drawn on the device): the pieces are not the oracle's, so
+    the rollout, the advantages and the policy -- which does not see this
+    iteration's critic update -- are compared with it, and the critic is held
+    to what tests/test_minibatch_gpu.py holds it to: the fused minibatch
+    epochs ran, and the same seeds give the same parameters bit for bit."""
+    out = []
+    for _ in range(2):
+        agent, _, _ = _agent_vs_oracle(
+            True, True, False, "metaworld", 5, num_env=11, epochs=2,
+            episodes=2, num_minibatchs=4, minibatch_permutation="device",
+            critic_vs_oracle=False)
+        assert tuple(agent.last_critic_plan)[:2] == ("fused-narrow", 4)
+        out.append(torch.cat([p.detach().reshape(-1)
+                              for p in agent.critic.parameters]).clone())
+    assert torch.isfinite(out[0]).all()
+    assert torch.equal(out[0], out[1])
 
 
 @pytest.mark.parametrize("env,nb,dtype,N,iters", [
@@ -331,36 +475,40 @@ def test_large_batch_step_matches_cpu_oracle(env, nb, dtype, N, iters,
 
 @pytest.mark.parametrize("env,nb", [("metaworld", 5), ("table_tennis", 3)])
 def test_deterministic_evaluation_matches_cpu_oracle(env, nb):
+    _evaluation_vs_oracle(env, nb)
+
+
+def test_deterministic_evaluation_of_two_episodes_matches_cpu_oracle():
+    _evaluation_vs_oracle("table_tennis", 3, test_episodes=2)
+
+
+def _evaluation_vs_oracle(env, nb, test_episodes=1):
     """f4: AbstractAgent.evaluate (abstract_agent.py:219-255) =
     one deterministic test rollout (use_mean, temporal_correlated_sampler.py:
     305-315): the trajectory of the mean parameters, raw (un-normalised) states
     into the critic, observation statistics untouched, pair offsets drawn --
-    after one training step, against the CPU oracle's evaluate()."""
+    after one training step, against the CPU oracle's evaluate().
+    test_episodes 2: ``episodes_per_test_env``, every episode from its own
+    reset, rows concatenated over the episodes."""
     from oracle.agent_oracle import OracleTCE
     N = 16
-    agent, cfg = build(N, 2, True, env=env, num_basis=nb)
-    oracle = OracleTCE(cfg["params"], N)
+    agent, cfg = build(N, 2, True, env=env, num_basis=nb,
+                       test_episodes=test_episodes)
+    oracle = OracleTCE(cfg["params"], N, test_episodes=test_episodes)
     with torch.no_grad():
         for po, pg in zip(oracle.pnet, agent.policy.mean_net.parameters()):
             po.copy_(pg.cpu())
         for po, pg in zip(oracle.cnet, agent.critic.net.parameters()):
             po.copy_(pg.cpu())
         oracle.var.copy_(agent.policy.variance_net.variable.cpu())
-    g = torch.Generator().manual_seed(9)
-    dof = agent.policy.num_dof
-    goal = torch.rand(N, dof, generator=g) * 2 - 1
-    pos0 = 0.1 * (torch.rand(N, dof, generator=g) * 2 - 1)
-    eps = torch.randn(N, agent.policy.dim_out, generator=g)
-    for e in (agent.sampler.train_envs, agent.sampler.test_envs):
-        def reset(e=e):
-            e.goal = goal.cuda()
-            z = torch.zeros(N, dof, device="cuda")
-            return e._obs(torch.zeros(N, device="cuda"), pos0.cuda(), z)
-        e.reset = reset
-    orig_sample = agent.policy.sample
-    agent.policy.sample = lambda **kw: orig_sample(
-        **kw, **({} if kw.get("use_mean") else {"eps": eps.cuda()}))
-    oracle.forced_reset, oracle.forced_eps = (goal, pos0), eps
+    # (the training rollout: one episode from the first reset; the evaluation:
+    # test_episodes episodes from the first resets of the same list)
+    resets, eps = _forced_state(N, agent.policy.num_dof, agent.policy.dim_out,
+                                torch.float32, test_episodes, 9)
+    _force_resets(agent.sampler.train_envs, [resets[0]], torch.float32)
+    _force_resets(agent.sampler.test_envs, resets, torch.float32)
+    _force_noise(agent.policy, eps[:1])
+    oracle.forced_reset, oracle.forced_eps = resets, eps[0]
     torch.manual_seed(11)
     agent.step()
     torch.manual_seed(11)
@@ -387,6 +535,9 @@ def test_deterministic_evaluation_matches_cpu_oracle(env, nb):
     _close("eval log_prob", c("segment_log_prob_estimate"),
            ref["segment_log_prob_estimate"], 1e-5)
     assert torch.equal(c("success"), ref["success"])
+    assert c("step_actions").shape[0] == N * test_episodes
+    if test_episodes > 1:       # the episodes are not copies of each other
+        assert not torch.allclose(c("step_actions")[:N], c("step_actions")[N:])
     # deterministic: the trajectory is the one of the mean parameters
     mean = det["segment_params_mean"]
     from tce_rl_amd import ops
@@ -452,14 +603,17 @@ BB_MP = dict(num_dof=4, num_basis=4, tau=5.0, alpha_phase=3, alpha=10,
 
 
 def build_bbrl(num_env, epochs, policy_hidden=(32, 2), critic_hidden=(32, 2),
-               act="relu", std_only=True, dtype="float32", **agent_kw):
-    """policy_hidden / critic_hidden: (neurons, hidden layers)."""
+               act="relu", std_only=True, dtype="float32", episodes=1,
+               **agent_kw):
+    """policy_hidden / critic_hidden: (neurons, hidden layers); episodes: the
+    sampler's ``episodes_per_train_env``."""
     from tce_rl_amd.rl import (agent_factory, critic_factory, policy_factory,
                                projection_factory, sampler_factory)
     mp = {"type": "prodmp", "args": dict(BB_MP, dtype=dtype, device="cuda")}
     sampler = sampler_factory("BlackBoxSampler",
                               env_id="metaworld_ProDMP/push-v2",
                               num_env_train=num_env, num_env_test=16,
+                              episodes_per_train_env=episodes,
                               dtype=dtype, device="cuda", seed=0, mp=mp,
                               task_specified_metrics=["success"])
     d_in = sampler.observation_shape[-1]
@@ -557,14 +711,25 @@ def test_bbrl_kept_graphs_equal_fresh_graphs_over_iterations():
 @pytest.mark.parametrize("mode", ["small", "op_by_op", "fused",
                                   "small_minibatch3"])
 def test_bbrl_step_matches_cpu_oracle(mode, monkeypatch):
+    _bbrl_step_vs_oracle(mode, monkeypatch)
+
+
+@pytest.mark.parametrize("mode", ["small", "small_minibatch3"])
+def test_bbrl_step_matches_cpu_oracle_two_episodes(mode, monkeypatch):
+    _bbrl_step_vs_oracle(mode, monkeypatch, episodes=2)
+
+
+def _bbrl_step_vs_oracle(mode, monkeypatch, episodes=1):
     """One BlackBoxAgent.step() (a16) against the CPU oracle step on the same
     weights, env state and parameter noise: on the hand-written row kernels of
     csrc/smlp.hip (the default), op by op under autograd, and with the
-    objective as one autograd node."""
+    objective as one autograd node.  episodes 2: two episodes per env, each
+    from its own reset with its own noise (black_box_sampler.py:158-249) --
+    N * 2 = 22 rows, not a multiple of what the row kernels tile by."""
     from oracle.agent_oracle import OracleBBRL
     from tce_rl_amd import smlp_ops
-    N, EPOCHS = 24, 3
-    agent, d_in = build_bbrl(N, EPOCHS)
+    N, EPOCHS = (24, 3) if episodes == 1 else (11, 3)
+    agent, d_in = build_bbrl(N, EPOCHS, episodes=episodes)
     agent.evaluation_interval = 0
     # small_minibatch3: the critic's minibatches (black_box_agent.py:124-131;
     # the class default is 10) on the row kernels, gathered pieces of numpy's
@@ -584,27 +749,18 @@ def test_bbrl_step_matches_cpu_oracle(mode, monkeypatch):
     # check, black_box_agent.py:218-284; the other two paths do not have it)
     oracle = OracleBBRL(BB_MP, N, d_in, [32, 32], [32, 32], "relu", True, 1e-5,
                         0.01, 3e-4, EPOCHS, 0.005, 0.0005, 1.0, True,
-                        balance=mode == "small", num_minibatchs=nmb)
+                        balance=mode == "small", num_minibatchs=nmb,
+                        episodes=episodes)
     with torch.no_grad():
         for po, pg in zip(oracle.pnet, agent.policy.mean_net.parameters()):
             po.copy_(pg.cpu())
         for po, pg in zip(oracle.cnet, agent.critic.net.parameters()):
             po.copy_(pg.cpu())
         oracle.var.copy_(agent.policy.variance_net.variable.cpu())
-    g = torch.Generator().manual_seed(3)
-    goal = torch.rand(N, 4, generator=g) * 2 - 1
-    pos0 = 0.1 * (torch.rand(N, 4, generator=g) * 2 - 1)
-    eps = torch.randn(N, 20, generator=g)
-    env = agent.sampler.train_envs
-
-    def reset():
-        env.goal = goal.cuda()
-        z = torch.zeros(N, 4, device="cuda")
-        return env._obs(torch.zeros(N, device="cuda"), pos0.cuda(), z)
-    env.reset = reset
-    sample = agent.policy.sample
-    agent.policy.sample = lambda **kw: sample(**kw, eps=eps.cuda())
-    oracle.forced_reset, oracle.forced_eps = (goal, pos0), eps
+    resets, eps = _forced_state(N, 4, 20, torch.float32, episodes, 3)
+    _force_resets(agent.sampler.train_envs, resets, torch.float32)
+    _force_noise(agent.policy, eps)
+    oracle.forced_reset, oracle.forced_eps = resets, eps
     captured = {}
     pd = agent.process_dataset
 
@@ -619,6 +775,7 @@ def test_bbrl_step_matches_cpu_oracle(mode, monkeypatch):
     np.random.seed(5)
     oracle.step()
     ref = oracle.last
+    assert captured["segment_action"].shape[0] == N * episodes
     _check_bbrl_metrics(res, oracle, 2e-4, balance=mode == "small")
     # float32 rounding only: bounds = 10-30 x the largest deviation seen
     # (32-wide nets, diagonal covariance: shorter sums than the TCE step)
@@ -697,6 +854,24 @@ BBRL_MID = {
 @pytest.mark.parametrize("balance,nmb", [(False, 1), (True, 1), (False, 4)])
 @pytest.mark.parametrize("shape", sorted(BBRL_MID))
 def test_bbrl_midsize_nets_match_cpu_oracle(shape, balance, nmb, monkeypatch):
+    _bbrl_midsize_vs_oracle(shape, balance, nmb, monkeypatch)
+
+
+@pytest.mark.parametrize("shape,nmb", [("box_push", 1), ("table_tennis", 4)])
+def test_bbrl_midsize_nets_match_cpu_oracle_two_episodes(shape, nmb,
+                                                         monkeypatch):
+    """The same with two episodes per env, each from its own reset with its own
+    noise: 11 x 2 = 22 rows through the matrix-core critic epochs / the row
+    kernels and the one-call policy epochs, at the one-episode tolerances.
+    (float32 shapes only: the float64 shapes' 1e-10 bound on the episode
+    return holds for the 24 env states of the one-episode cases, other states
+    -- 11 envs, ONE episode -- reach 4e-9 of max |return| in single rows.)"""
+    _bbrl_midsize_vs_oracle(shape, False, nmb, monkeypatch, num_env=11,
+                            episodes=2)
+
+
+def _bbrl_midsize_vs_oracle(shape, balance, nmb, monkeypatch, num_env=24,
+                            episodes=1):
     """One BlackBoxAgent.step() with the reference's OTHER black-box nets -- box
     pushing's 128 x 2 policy / 256 x 2 critic, table tennis's 256 x 1 / 256 x 1
     (full covariance, leaky relu, weight decay) -- against the CPU oracle: the
@@ -710,11 +885,12 @@ def test_bbrl_midsize_nets_match_cpu_oracle(shape, balance, nmb, monkeypatch):
     cfg = BBRL_MID[shape]
     # (balance: more and larger steps, so that the trust region becomes active
     # and its loss has a gradient to measure)
-    N, EPOCHS, LR = (24, 6, 3e-3) if balance else (24, 3, 3e-4)
+    N, EPOCHS, LR = (num_env, 6, 3e-3) if balance else (num_env, 3, 3e-4)
     dt = getattr(torch, cfg["dtype"])
     agent, d_in = build_bbrl(
         N, EPOCHS, cfg["policy_hidden"], cfg["critic_hidden"], cfg["act"],
-        cfg["std_only"], cfg["dtype"], wd_policy=cfg["wd"], wd_critic=cfg["wd"],
+        cfg["std_only"], cfg["dtype"], episodes=episodes,
+        wd_policy=cfg["wd"], wd_critic=cfg["wd"],
         clip_critic=cfg["clip_critic"], balance_check=25 if balance else False,
         lr_policy=LR, lr_critic=LR)
     agent.evaluation_interval = 0
@@ -741,27 +917,17 @@ def test_bbrl_midsize_nets_match_cpu_oracle(shape, balance, nmb, monkeypatch):
                         1e-5, 0.01, LR, EPOCHS, 0.005, 0.0005, 1.0, True,
                         clip_critic=cfg["clip_critic"], dtype=dt,
                         balance=balance, weight_decay=cfg["wd"],
-                        num_minibatchs=nmb)
+                        num_minibatchs=nmb, episodes=episodes)
     with torch.no_grad():
         for po, pg in zip(oracle.pnet, agent.policy.mean_net.parameters()):
             po.copy_(pg.cpu())
         for po, pg in zip(oracle.cnet, agent.critic.net.parameters()):
             po.copy_(pg.cpu())
         oracle.var.copy_(agent.policy.variance_net.variable.cpu())
-    g = torch.Generator().manual_seed(3)
-    goal = (torch.rand(N, 4, generator=g) * 2 - 1).to(dt)
-    pos0 = (0.1 * (torch.rand(N, 4, generator=g) * 2 - 1)).to(dt)
-    eps = torch.randn(N, 20, generator=g).to(dt)
-    env = agent.sampler.train_envs
-
-    def reset():
-        env.goal = goal.cuda()
-        z = torch.zeros(N, 4, device="cuda", dtype=dt)
-        return env._obs(torch.zeros(N, device="cuda", dtype=dt), pos0.cuda(), z)
-    env.reset = reset
-    sample = agent.policy.sample
-    agent.policy.sample = lambda **kw: sample(**kw, eps=eps.cuda())
-    oracle.forced_reset, oracle.forced_eps = (goal, pos0), eps
+    resets, eps = _forced_state(N, 4, 20, dt, episodes, 3)
+    _force_resets(agent.sampler.train_envs, resets, dt)
+    _force_noise(agent.policy, eps)
+    oracle.forced_reset, oracle.forced_eps = resets, eps
     captured = {}
     pd = agent.process_dataset
 
@@ -776,6 +942,7 @@ def test_bbrl_midsize_nets_match_cpu_oracle(shape, balance, nmb, monkeypatch):
     np.random.seed(5)
     oracle.step()
     ref = oracle.last
+    assert captured["segment_action"].shape[0] == N * episodes
     f64 = dt == torch.float64
     # float32: rounding of 128- / 256-term sums; float64: the basis table and the
     # projection's Newton iteration stop at 1e-10 .. 1e-12, Adam's first steps
@@ -1142,8 +1309,21 @@ def test_step_from_the_references_resolved_documents(doc):
     agent = exp.agent
     assert agent.policy.dim_out == dim_policy_out(p)
     assert type(agent).__name__ == p["agent"]["type"]
-    for _ in range(2):
+    # several episodes per env (5 in three of the documents, 2 in one): the
+    # dataset the agent works on has one row per env AND episode, and every
+    # one of those episodes is counted in the env steps
+    episodes = int(sa.get("episodes_per_train_env", 1))
+    assert agent.sampler.episodes_per_train_env == episodes
+    rows = []
+    pd = agent.process_dataset
+    agent.process_dataset = lambda ds: (
+        rows.append(ds["segment_state"].shape[0]), pd(ds))[1]
+    T = agent.sampler.train_envs.num_times
+    for it in range(2):
         res = agent.step()
+        assert agent.num_global_steps == (it + 1) * 32 * episodes * T
+        assert res["num_global_steps"] == agent.num_global_steps
+    assert rows == [32 * episodes] * 2
     for k in ("critic_loss_mean", "surrogate_loss_mean", "policy_loss_mean",
               "trust_region_loss_mean", "entropy_mean"):
         assert np.isfinite(res[k]), k

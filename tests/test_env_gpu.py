@@ -214,3 +214,52 @@ def test_sampler_accepts_an_env_without_the_fused_capability():
     for k in ("step_states", "step_values", "step_rewards", "step_actions",
               "segment_log_prob_estimate"):
         torch.testing.assert_close(b[k], a[k], rtol=2e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_rms_merge_of_several_batches_about_the_running_mean(dtype):
+    """What a rollout of several episodes does to the observation statistics:
+    one merge per episode, each batch's moment partials accumulated about the
+    running mean OF THAT MOMENT (a non-empty state from the second merge on),
+    batches of different row counts and partial counts.  Against the float64
+    chain of update_from_moments over the same batches, and the mean against
+    the one-pass float64 sum over all rows seen so far (the chain's mean is
+    exactly sum / (1e-4 + rows))."""
+    from tce_rl_amd import ops
+    D = 35
+    g = torch.Generator().manual_seed(5)
+    mean = torch.zeros(D, dtype=dtype).cuda()
+    var = torch.ones(D, dtype=dtype).cuda()
+    count = 1e-4
+    rms = O.RunningMeanStd((D,), torch.float64)
+    seen = []
+    mtol = dict(rtol=1e-5, atol=1e-6) if dtype == torch.float32 \
+        else dict(rtol=1e-10, atol=1e-12)
+    for b, (rows, nparts) in enumerate(((1503, 7), (64, 1), (40000, 300))):
+        # (rows in the state's dtype, as the env kernel writes them; every
+        # batch from another distribution, so the mean moves)
+        x = (torch.randn(rows, D, generator=g, dtype=torch.float64) * (1 + b)
+             + 3.0 * b - 1).to(dtype).double()
+        shift = mean.clone()
+        k = shift.cpu().double()
+        partials = torch.stack([
+            torch.stack([(c - k).sum(0), ((c - k) ** 2).sum(0)], -1)
+            for c in x.tensor_split(nparts)])
+        assert partials.shape == (nparts, D, 2)
+        # (second batch: the default shift, the running mean itself, which
+        # the kernel then reads and overwrites)
+        count = ops.rms_merge(partials.cuda(), rows, mean, var, count,
+                              shift=None if b == 1 else shift)
+        rms.update(x)
+        seen.append(x)
+        every = torch.cat(seen)
+        assert count == pytest.approx(1e-4 + every.shape[0], rel=1e-14)
+        assert count == pytest.approx(rms.count, rel=1e-14)
+        torch.testing.assert_close(mean.cpu().double(),
+                                   every.sum(0) / (1e-4 + every.shape[0]),
+                                   **mtol)
+        torch.testing.assert_close(mean.cpu().double(), rms.mean, **mtol)
+        torch.testing.assert_close(var.cpu().double(), rms.var, **mtol)
+    # (the chain is, up to the 1e-4 pseudo-count and n / (n - 1), the variance
+    # over all rows)
+    assert abs(every.var(0, unbiased=False) - rms.var).max() < 1e-2
