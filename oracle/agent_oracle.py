@@ -53,8 +53,14 @@ class OracleTCE:
         self.dof, self.K = self.mp.num_dof, self.mp.num_dof * self.mp.num_basis_g
         self.N, self.dt = num_env, self.mp.dt
         self.T = {0.0125: 500, 0.02: 100, 0.008: 350}[self.dt]
+        if "HopperJump" in str(cfg.get("sampler", {}).get("args", {}).get(
+                "env_id", "")):
+            self.T = 250                # shares dt 0.008 with table tennis
         self.task, self.d_task = E.FAMILY[self.T]
         self.D = self.d_task + 1 + 2 * self.dof
+        # the reference's resolved documents carry these as YAML strings
+        a = dict(a, **{k: float(a[k]) for k in (
+            "lr_policy", "lr_critic", "wd_policy", "wd_critic") if k in a})
         self.a = a
         pa, ca = cfg["policy"]["args"], cfg["critic"]["args"]
         d_in = self.D - 2 * self.dof
@@ -166,7 +172,8 @@ class OracleTCE:
                 states, rewards, flags, metrics = E.rollout(
                     self.task, actions, s0, self.dof, self.d_task, self.dt)
                 episode_reward = rewards.sum(-1)
-                if self.task == "table_tennis":  # make_mdp_reward on hit_ball
+                # make_mdp_reward on hit_ball / has_left_floor
+                if self.task in ("table_tennis", "hopper"):
                     rewards = O.make_mdp_reward(rewards, flags)
                 if training:
                     self.rms.update(states.view(-1, self.D))

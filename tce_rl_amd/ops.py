@@ -262,14 +262,20 @@ def _times_flags(mp, times_, init_time):
     return general | (2 if ready else 0)
 
 
-def prodmp_traj(mp, times_, params, init_time, init_pos, init_vel):
-    """cat[pos, vel] [N, T, 2*dof] of the ProDMP with parameters [N, K]."""
+def prodmp_traj(mp, times_, params, init_time, init_pos, init_vel, out=None):
+    """cat[pos, vel] [N, T, 2*dof] of the ProDMP with parameters [N, K].
+    out: a contiguous, 16-byte aligned tensor of that shape to write into."""
     check_dev(times_, params, init_time, init_pos, init_vel)
     t, p = _c(times_), _c(mp.pad_params(params))
     t0, y0, v0 = _c(init_time), _c(init_pos), _c(init_vel)
     N, T = t.shape
     assert p.shape == (N, mp.num_dof * mp.num_basis_g)
-    out = torch.empty(N, T, 2 * mp.num_dof, dtype=p.dtype, device=p.device)
+    if out is None:
+        out = torch.empty(N, T, 2 * mp.num_dof, dtype=p.dtype, device=p.device)
+    else:
+        check_dev(out)
+        assert out.shape == (N, T, 2 * mp.num_dof) and out.dtype == p.dtype \
+            and out.is_contiguous() and out.data_ptr() % 16 == 0
     B, flag = _mp_ws(mp, T, p.device)
     general = _times_flags(mp, t, t0)
     call("tce_prodmp_traj_" + sfx(p.dtype), *mp.c_args(), ptr(t), general,

@@ -67,15 +67,17 @@ def _force_noise(policy, eps):
 
 
 def build(num_env, epochs, overlap, env="metaworld", num_basis=5,
-          dtype="float32", episodes=1, test_episodes=1, **agent_kw):
+          dtype="float32", episodes=1, test_episodes=1, cfg=None, **agent_kw):
     """agent_kw: agent constructor arguments; the keys ``_contextual`` /
     ``_std_only`` switch the policy's covariance head instead.  episodes /
     test_episodes: the sampler's ``episodes_per_train_env`` /
-    ``episodes_per_test_env``."""
+    ``episodes_per_test_env``.  cfg: a ready experiment document (with its own
+    env count, epochs and dtype) instead of tce_config's."""
     from tce_rl_amd.config import tce_config
     from tce_rl_amd.mp_exp import MPExperiment
-    cfg = tce_config(env, num_env=num_env, num_basis=num_basis, epochs=epochs,
-                     evaluation_interval=0, dtype=dtype)
+    if cfg is None:
+        cfg = tce_config(env, num_env=num_env, num_basis=num_basis,
+                         epochs=epochs, evaluation_interval=0, dtype=dtype)
     cfg["params"]["sampler"]["args"].update(
         episodes_per_train_env=episodes, episodes_per_test_env=test_episodes)
     agent_kw = dict(agent_kw)
@@ -230,6 +232,38 @@ def test_agent_step_matches_cpu_oracle_other_shapes(env, nb, dtype):
     -- with the reference's 3 basis functions (K 28) and with the 8 that
     BASELINE.json configs[4] states (K 63)."""
     _agent_vs_oracle(True, True, False, env, nb, dtype)
+
+
+def test_agent_step_matches_cpu_oracle_hopper_document():
+    """The one shipped document whose shape no other oracle comparison has:
+    tests/golden/resolved/hopper_jump_tcp.json -- float64, dof 3, 3 basis
+    functions (K 12: run-time-shape trajectory rows kernel with 8-byte chunks,
+    LDS form of the pair kernels at R 6), T 250, has_left_floor reward
+    re-shaping -- shrunk to 6 envs x 2 episodes and 3 + 3 epochs, two
+    iterations, at the float64 tolerances of the other cases."""
+    import json
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    d = json.load(open(os.path.join(here, "golden", "resolved",
+                                    "hopper_jump_tcp.json")))
+    p, N, EPOCHS = d["params"], 6, 3
+    assert p["mp"]["args"]["num_dof"] == 3 and \
+        p["mp"]["args"]["num_basis"] == 3 and \
+        p["agent"]["args"]["dtype"] == "float64"
+    for blk in p.values():
+        blk["args"]["device"] = "cuda"
+    p["sampler"]["args"].update(num_env_train=N, num_env_test=N,
+                                task_specified_metrics=["success"])
+    p["agent"]["args"].update(epochs_policy=EPOCHS, epochs_critic=EPOCHS,
+                              evaluation_interval=0)
+    p["policy"]["args"]["mp"] = p["mp"]
+    cfg = {"name": d["name"], "seed": 0, "iterations": d["iterations"],
+           "params": p}
+    agent, oracle, _ = _agent_vs_oracle(
+        True, True, False, "hopper", 3, "float64", iterations=2, num_env=N,
+        epochs=EPOCHS, episodes=2, cfg=cfg)
+    assert agent.sampler.num_times == oracle.T == 250
+    assert agent.policy.num_dof == 3 and agent.policy.dim_out == 12
 
 
 @pytest.mark.parametrize("overlap", [False, True])

@@ -5,8 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+import prodmp_cases as cases
 from oracle import tce_oracle as O
 from oracle.prodmp_oracle import ProDMPOracle, pair_log_prob
+from prodmp_cases import affine
 
 pytestmark = pytest.mark.gpu
 T_ = torch.as_tensor
@@ -38,35 +40,11 @@ def ops():
 
 
 def make(name, dtype):
-    from tce_rl_amd.mp import ProDMP
-    return ProDMP(dtype=dtype, device="cuda", **CFGS[name]), \
-        ProDMPOracle(dtype=dtype, **CFGS[name])
-
-
-def affine(times_cpu):
-    """The oracle's own time grid on the GPU, tagged like ops.times() output:
-    isolates the kernels under test from the last-bit differences of the
-    float32 linspace weights (machine dependent on the CPU side)."""
-    t = times_cpu.cuda()
-    t._tce_affine = True
-    return t
+    return cases.make(CFGS[name], dtype)
 
 
 def inputs(name, N, dtype, seed=0, uniform_t0=True):
-    cfg = CFGS[name]
-    dof, K = cfg["num_dof"], cfg["num_dof"] * (cfg["num_basis"] + 1)
-    g = torch.Generator().manual_seed(seed)
-    rn = lambda *s: torch.randn(*s, generator=g, dtype=dtype)
-    mean = 0.5 * rn(N, K)
-    L = O.vector_to_cholesky(
-        torch.cat([rn(N, K), 0.05 * rn(N, K * (K - 1) // 2)], -1), K, 1e-4,
-        False)
-    eps = rn(N, K)
-    y0 = torch.rand(N, dof, generator=g, dtype=dtype) * 2 - 1
-    v0 = 0.1 * rn(N, dof)
-    t0 = torch.zeros(N, dtype=dtype) if uniform_t0 else \
-        torch.rand(N, generator=g, dtype=dtype) * 0.2
-    return mean, L, eps, t0, y0, v0
+    return cases.inputs(CFGS[name], N, dtype, seed, uniform_t0)
 
 
 def test_times_golden(ops, golden):
